@@ -24,6 +24,9 @@ PyTorch-CPU port of the reference path, timed on this host's cores on a bounded 
 N = 1 line also carries ``ref_dims``: the reference-YAML-dims workloads hlg_ref and grid_ref (= BASELINE configs[0]) measured by
 child runs of this script.  Multi-rank lines carry ``rccl_ranks_seen``, ``collective_backend``,
 ``allreduce_ms`` and ``allreduce_buckets``.
+
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (``dump_outputs``); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -243,6 +246,32 @@ def route_overhead(rows_share, timeout_s=150):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, up):
+    """--dump-outputs DIR: what the last timed step computed, as the caller of that step holds it afterwards -- the updated
+    parameters and Adam moments (flat buffers in the engine's parameter-table order), the step's gradient and its four loss
+    scalars (loss, value, surrogate, entropy), and the per-row value / log-prob / entropy of the minibatch forward -- one float32
+    DIR/<name>.npy each.  Returns {name: bytes}."""
+    engine = up.engine
+    nflt = engine.n_floats
+    if getattr(up, '_lane_bufs', None) is not None and up.lanes > 1:      # UPAMD_LANES=2: the two halves, in row order
+        rows = [torch.cat([bufs[i] for bufs, _ in up._lane_bufs]) for i in range(3)]
+    else:
+        rows = up._rows[:3]
+    arrays = {'params': up.flat, 'adam_exp_avg': up.m, 'adam_exp_avg_sq': up.v, 'grads': up.grads[:nflt],
+              'losses': up.grads[nflt:nflt + 4], 'row_value': rows[0], 'row_log_prob': rows[1], 'row_entropy': rows[2]}
+    host = {name: t.detach().to(torch.float32).cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: int(a.nbytes) for name, a in host.items()}
+
+
 REF_DIMS_KEYS = ('value', 'unit', 'ms_per_step', 'steps', 'warmup', 'node_steps_per_s', 'host_enqueue_ms_per_step', 'kernel_ms_per_step')
 
 
@@ -305,7 +334,12 @@ def main():
                          'report strong_proxy = ms(full) / (ms(share) + exposed all-reduce); auto = for the default workload only')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                     help='weak (default): the minibatch per GPU is fixed; strong: the GLOBAL minibatch is fixed and split')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (parameters, Adam moments, gradient, loss '
+                         'scalars, per-row value / log-prob / entropy) as DIR/<name>.npy, float32 (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         spawn_ranks(args, sys.argv[1:])             # does not return: this process becomes the launcher
     # The learner process of the reference runs with OMP_NUM_THREADS=1 (khrylib/rl/agents/agent.py:12).  It matters here: torch's
@@ -431,6 +465,7 @@ def main():
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     ctx.all_reduce_max(tmax)
     dt = float(tmax.item())
+    dumped = dump_outputs(args.dump_outputs, up) if args.dump_outputs and rank == 0 else None
 
     # ---- strong-scaling proxy on one GPU (north-star: >= 6x at 8 GPUs): the same resident replay stepped at 1/8 of the
     # minibatch = what each of 8 ranks computes per optimizer step of a strong-scaling run (dp 'global': B / world rows per rank)
@@ -561,6 +596,8 @@ def main():
                                             '--inclusive-pool (then the packer re-reads a small working set: an upper bound)'},
         'dp_mode': incl.get('dp_mode'),
     }
+    if dumped is not None:
+        out['dump_outputs'] = {'dir': os.path.abspath(args.dump_outputs), 'bytes': dumped}
     if incl_rec is not None:
         out['update_params_inclusive_records'] = {
             'samples_per_s': incl_rec['steps'] * incl_rec['rows_per_step'] / incl_rec['seconds'], 'seconds': incl_rec['seconds'],

@@ -86,3 +86,30 @@ def test_route_overhead_is_the_difference_of_three_child_runs(monkeypatch):
         return subprocess.CompletedProcess(cmd, 1, '', 'no rccl')
     monkeypatch.setattr(subprocess, 'run', failing)
     assert 'error' in bench.route_overhead(256)
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_as_float32(tmp_path):
+    """--dump-outputs: the updater's buffers as the last step left them, one float32 .npy each, the loss scalars split off the
+    gradient buffer's tail."""
+    import types
+    import numpy as np
+    import torch
+    n = 10
+    g = torch.Generator().manual_seed(0)
+    up = types.SimpleNamespace(engine=types.SimpleNamespace(n_floats=n), lanes=1, _lane_bufs=None,
+                               flat=torch.randn(n, generator=g), m=torch.randn(n, generator=g), v=torch.rand(n, generator=g),
+                               grads=torch.randn(n + 4, generator=g), _rows=[torch.randn(6, generator=g) for _ in range(6)])
+    sizes = bench.dump_outputs(str(tmp_path / 'dump'), up)
+    assert sorted(sizes) == sorted(os.path.splitext(f)[0] for f in os.listdir(str(tmp_path / 'dump')))
+    load = lambda name: np.load(str(tmp_path / 'dump' / (name + '.npy')))
+    assert all(load(k).dtype == np.float32 for k in sizes)
+    assert np.array_equal(load('params'), up.flat.numpy()) and np.array_equal(load('adam_exp_avg_sq'), up.v.numpy())
+    assert np.array_equal(load('grads'), up.grads[:n].numpy()) and np.array_equal(load('losses'), up.grads[n:].numpy())
+    assert np.array_equal(load('row_log_prob'), up._rows[1].numpy()) and sizes['row_entropy'] == 6 * 4
+
+
+def test_steps_below_one_are_refused_before_any_device_work():
+    import subprocess
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '0', '--warmup', '1'],
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 2 and '--steps must be >= 1' in res.stderr and not res.stdout

@@ -1,13 +1,15 @@
-"""The oracle against the LIVE reference (build container only: skipped wherever /root/reference is absent, e.g. on
-the GPU box).  Two things are pinned here that the committed golden vectors cannot pin:
+"""The oracle against the LIVE reference.  Two things are pinned here that the golden vectors of the fixed cases cannot pin:
 
-* the oracle's ``update_params`` reproduces the reference's on a freshly generated replay (not only on the three
-  golden cases), loss by loss;
+* the oracle's ``update_params`` reproduces the reference's on a freshly generated replay (not only on the
+  golden cases), loss by loss.  The reference's run on that replay is stored in ``tests/golden/live_fresh.npz``
+  (``python tests/test_reference_live.py`` regenerates it with the real reference), so the oracle is checked against it
+  everywhere; where the reference tree is importable the live run is compared as well;
 * ``bench.py``'s ``cpu_baseline`` times the ORACLE (``kind: "port"``) because the reference cannot travel to the GPU
   box -- so the port must cost what the reference costs: the wall time of the oracle's update loop has to be within
   10 % of ``UrbanPlanningAgent.update_params`` (urban_planning_agent.py:248-361) on the same replay, thread count and
-  minibatch schedule.
+  minibatch schedule.  This one needs the reference tree itself (skipped where it is absent).
 """
+import os
 import time
 
 import numpy as np
@@ -18,9 +20,10 @@ import helpers
 from oracle import ref_import
 from oracle import sgnn_oracle as orc
 
-pytestmark = pytest.mark.skipif(not ref_import.available(), reason='/root/reference is not present')
+needs_reference = pytest.mark.skipif(not ref_import.available(), reason='the reference tree is not present')
 
 SPEC = dict(D=32, L=2, heads=1, max_nodes=300, max_edges=900)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'live_fresh.npz')
 
 
 def _pair(seed=0):
@@ -41,20 +44,45 @@ def _replay(T=96):
                              road_fraction=0.25, n_range=(120, 280))
 
 
+def _reference_run():
+    """The live reference's update_params on the fresh replay: initial weights, the 'loss/loss' scalars, weights after."""
+    ag, _ = _pair()
+    sd0 = {k: v.detach().clone() for k, v in ag.actor_critic_net.state_dict().items()}
+    np.random.seed(5)
+    ag.update_params(_replay(), 0)
+    losses = np.array([v for (tag, v, s) in ag.tb_logger.scalars if tag == 'loss/loss'])
+    sd1 = {k: v.detach().clone() for k, v in ag.actor_critic_net.state_dict().items()}
+    return sd0, losses, sd1
+
+
+def _load_golden():
+    z = np.load(GOLDEN)
+    sd0 = {k[len('init/'):]: torch.from_numpy(z[k]) for k in z.files if k.startswith('init/')}
+    sd1 = {k[len('upd/'):]: torch.from_numpy(z[k]) for k in z.files if k.startswith('upd/')}
+    return sd0, z['losses'], sd1
+
+
 def test_oracle_update_matches_the_live_reference_on_a_fresh_replay():
-    ag, ou = _pair()
-    replay = _replay()
+    sd0, ref_losses, sd1 = _load_golden()
+    ou = orc.OracleUpdater(helpers.oracle_params(sd0), num_optim_epoch=2, mini_batch_size=32, num_heads=SPEC['heads'])
     np.random.seed(5)
-    ag.update_params(replay, 0)
-    np.random.seed(5)
-    ou.update_params(replay)
-    ref_losses = np.array([v for (tag, v, s) in ag.tb_logger.scalars if tag == 'loss/loss'])
+    ou.update_params(_replay())
     np.testing.assert_allclose(np.array(ou.loss_log)[:, 0], ref_losses, rtol=2e-5, atol=1e-6)
-    flat = orc.split_actor_critic_state_dict(ag.actor_critic_net.state_dict())
+    flat = orc.split_actor_critic_state_dict(sd1)
+    for k, p in ou.P.items():
+        np.testing.assert_allclose(p.detach().numpy(), flat[k].numpy(), rtol=1e-5, atol=2e-6, err_msg=k)
+    if not ref_import.available():
+        return
+    # the live reference: same initial weights as stored, and the oracle reproduces its run as well
+    live0, live_losses, live1 = _reference_run()
+    assert list(live0) == list(sd0) and all(torch.equal(live0[k], sd0[k]) for k in sd0)
+    np.testing.assert_allclose(np.array(ou.loss_log)[:, 0], live_losses, rtol=2e-5, atol=1e-6)
+    flat = orc.split_actor_critic_state_dict(live1)
     for k, p in ou.P.items():
         np.testing.assert_allclose(p.detach().numpy(), flat[k].numpy(), rtol=1e-5, atol=2e-6, err_msg=k)
 
 
+@needs_reference
 def test_oracle_step_time_is_the_reference_step_time():
     """min-of-N wall time of a whole update_params (6 optimizer steps of 32 padded rows + the two no-grad sweeps),
     interleaved reference / oracle so that machine noise hits both alike.  A shared build box is noisy (other jobs, the
@@ -81,3 +109,13 @@ def test_oracle_step_time_is_the_reference_step_time():
             break
     assert 0.90 <= ratio <= 1.10, 'oracle %.3f s vs reference %.3f s per update_params (ratio %.3f)' % (
         min(t_orc), min(t_ref), ratio)
+
+
+if __name__ == '__main__':
+    # regenerate tests/golden/live_fresh.npz from the real reference (needs the reference tree, oracle/ref_import.py)
+    sd0, losses, sd1 = _reference_run()
+    out = {'losses': losses}
+    out.update({'init/' + k: v.numpy() for k, v in sd0.items()})
+    out.update({'upd/' + k: v.numpy() for k, v in sd1.items()})
+    np.savez_compressed(GOLDEN, **out)
+    print('wrote %s (%d steps)' % (GOLDEN, len(losses)))
