@@ -152,21 +152,27 @@ extern "C" int upamd_tiny_profile(void *buf_dev) {
     return UPAMD_OK;
 }
 
+// an on / off knob: any other value is refused, not clamped (a lab command naming a retired setting must not measure the default)
+static int tune_on_off(const char *name, int32_t value, void (*set)(int)) {
+    if (value != 0 && value != 1) return fail(UPAMD_E_INVALID, "upamd_tune: '%s' is 0 or 1, not %d", name, (int)value);
+    set(value);
+    return UPAMD_OK;
+}
+
 extern "C" int upamd_tune(const char *name, int32_t value) {
     if (!name) return fail(UPAMD_E_INVALID, "upamd_tune: name is null");
-    if (!strcmp(name, "gemm_nt_dma")) { set_gemm_nt_dma_variant(value); return UPAMD_OK; }
+    if (!strcmp(name, "gemm_nt_dma")) return tune_on_off(name, value, set_gemm_nt_dma);
     if (!strcmp(name, "gemm_lds_pad")) { set_gemm_lds_pad(value); return UPAMD_OK; }
     if (!strcmp(name, "gemm_stagger_mode")) { set_gemm_stagger(value, -1); return UPAMD_OK; }
     if (!strcmp(name, "gemm_stagger_cycles")) { set_gemm_stagger(-1, value); return UPAMD_OK; }
-    if (!strcmp(name, "fold_layer1")) { set_fold_layer1(value); return UPAMD_OK; }
+    if (!strcmp(name, "fold_layer1")) return tune_on_off(name, value, set_fold_layer1);
     if (!strcmp(name, "pq_exp")) { set_pq_exp(value); return UPAMD_OK; }
     if (!strcmp(name, "bwd_nb_global")) { set_bwd_nb_global(value); return UPAMD_OK; }
     if (!strcmp(name, "nt_min_wgs")) { set_gemm_nt_min_wgs(value); return UPAMD_OK; }
     if (!strcmp(name, "gemm_split")) { set_gemm_nt_split(value); return UPAMD_OK; }
     if (!strcmp(name, "he_fused")) { set_he_feat_fused(value); return UPAMD_OK; }
-    if (!strcmp(name, "side_wgrad")) { set_side_wgrad(value); return UPAMD_OK; }
+    if (!strcmp(name, "side_wgrad")) return tune_on_off(name, value, set_side_wgrad);
     if (!strcmp(name, "grad_buckets")) { set_grad_buckets(value); return UPAMD_OK; }
-    if (!strcmp(name, "side_priority")) { set_side_priority(value); return UPAMD_OK; }
     if (!strcmp(name, "side_heads")) { set_side_heads(value); return UPAMD_OK; }
     if (!strcmp(name, "side_stream")) { set_side_stream(value); return UPAMD_OK; }
     if (!strcmp(name, "fwd_h_hbm")) { set_fwd_h_hbm(value); return UPAMD_OK; }

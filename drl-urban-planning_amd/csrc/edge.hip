@@ -688,14 +688,6 @@ void set_bwd_nb_global(int on) { g_bwd_nb_global = on ? 1 : 0; }
 static int g_fwd_h_hbm = 1;      // tune knob "fwd_h_hbm": the large size class of the forward keeps H in HBM (two workgroups per CU)
 void set_fwd_h_hbm(int on) { g_fwd_h_hbm = on ? 1 : 0; }
 
-// tune knob fold_layer1 = 2 (lab rule, not the default): fold only when the minibatch's largest graph fits HALF the LDS.  It
-// dates from when the folded kernels had no H-in-HBM / list-in-global forms and ran their large size class at one workgroup
-// per CU; they have both now (edge_fwd_kernel<.., FOLD, HLDS = false>, edge_bwd_kernel<.., FOLD, .., NBG>): DHM 115.5k ->
-// 119.0k samples/s, profiles/archive/r03_lab_fold_two_per_cu.log
-bool edge_fold_pays(const MbView &mb) {
-    return edge_lds_bytes(mb.max_n, mb.max_inc, false, false, true, true) <= LDS_HALF &&
-           edge_lds_bytes(mb.max_n, mb.max_inc, true, false, true, true) <= LDS_HALF;
-}
 bool edge_fold_ok(const MbView &mb) {
     return edge_lds_bytes(mb.max_n, mb.max_inc, false, false, true, true) <= LDS_LIMIT &&
            edge_lds_bytes(mb.max_n, mb.max_inc, true, false, true, true) <= LDS_LIMIT;

@@ -55,12 +55,11 @@ namespace {
 // tune knob "side_wgrad": the weight-gradient GEMM of GCN layer l on the side stream next to the same layer's dgrad GEMM (dP|dQ
 // alternates between two buffers).  Measured (profiles/archive/r03_lab_side_streams.log): two big GEMMs sharing the matrix pipe lose 2.5 %
 // of the 2048-row step, but at <= 256 rows per step neither GEMM fills the chip (2.9 rounds of workgroups) and running them
-// together gains 3 % -- so the default (1) applies it to minibatches of at most SIDE_WGRAD_MAX_NODES nodes; 2 = always, with the
-// weight gradient BEHIND the dgrad, i.e. next to the next layer's message passing (-2 %: the walk and the GEMM slow each other
-// more than they overlap); 3 = always next to the dgrad; 0 = never
+// together gains 3 % -- so the default (1) applies it to minibatches of at most SIDE_WGRAD_MAX_NODES nodes; 0 = never.  (The weight
+// gradient behind the dgrad, next to the next layer's message passing, measured +1.3 % per step: DESIGN section 5a.)
 static int g_side_wgrad = 1;
 constexpr int64_t SIDE_WGRAD_MAX_NODES = 98304;
-static bool side_wgrad_on(int64_t M) { return g_side_wgrad >= 2 || (g_side_wgrad == 1 && M <= SIDE_WGRAD_MAX_NODES); }
+static bool side_wgrad_on(int64_t M) { return g_side_wgrad && M <= SIDE_WGRAD_MAX_NODES; }
 constexpr int MAXL = 16;
 constexpr int MAXK = UPAMD_MAX_EDGE_FC;
 static inline int LK(int l, int k) { return (l - 1) * (MAXK + 1) + k; }      // l = 1 .. L, k = 0 .. MAXK
@@ -312,7 +311,6 @@ int check_args(upamd_engine *eng, const void *packed, const upamd_pack_layout *l
 // per-sample weight gradients only by the final reduction.  They run on an engine-owned side stream, forked from / joined to the
 // caller's stream with events, underneath the GCN layers' GEMM / message-passing launches (tune knob "side_stream", default on).
 static int g_side_stream = 1;
-static int g_side_priority = 1;
 static int side_ready(upamd_engine *eng, hipStream_t st, SideCtx **out) {
     SideCtx &c = eng->sides[st];
     if (!c.side) {
@@ -320,17 +318,16 @@ static int side_ready(upamd_engine *eng, hipStream_t st, SideCtx **out) {
         // creation order: with RCCL initialised (its own streams come first) the side stream landed on the SAME hardware queue as
         // the caller's stream and the forked step ran serialised (measured: no overlap, -3 %).  A stream of another priority
         // level lives in that level's own queues; high priority also suits what runs here -- short kernels that gate the caller's
-        // stream (tune knob "side_priority": 1 = high (default), 0 = normal, 2 = low).
+        // stream.
         int least = 0, greatest = 0;
         UPAMD_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (g_side_priority == 0 || least == greatest)
+        if (least == greatest) {
             UPAMD_HIP(hipStreamCreateWithFlags(&c.side, hipStreamNonBlocking));
-        else
-            UPAMD_HIP(hipStreamCreateWithPriority(&c.side, hipStreamNonBlocking, g_side_priority == 1 ? greatest : least));
-        if (g_side_priority == 0 || least == greatest)
             UPAMD_HIP(hipStreamCreateWithFlags(&c.side2, hipStreamNonBlocking));
-        else
-            UPAMD_HIP(hipStreamCreateWithPriority(&c.side2, hipStreamNonBlocking, g_side_priority == 1 ? greatest : least));
+        } else {
+            UPAMD_HIP(hipStreamCreateWithPriority(&c.side, hipStreamNonBlocking, greatest));
+            UPAMD_HIP(hipStreamCreateWithPriority(&c.side2, hipStreamNonBlocking, greatest));
+        }
         UPAMD_HIP(hipEventCreateWithFlags(&c.ev_join2, hipEventDisableTiming));
         UPAMD_HIP(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming));
         UPAMD_HIP(hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming));
@@ -428,14 +425,9 @@ static bool pq_exp_layer(const GemmNT &g, int l, int K) { return g_pq_exp && K =
 
 // slabs[s][I][J] = partial sums of A[rows, I](pm)^T * Bm[rows, J](pm): the tiled split-K MFMA kernel where the shape allows
 // (I % 128 == 0), otherwise one grouped-kernel launch with panel-major operands (narrow models: D = 16 ... 64)
-// tune knob "fold_layer1" (default on): first GCN layer computed inside the message-passing kernels
+// tune knob "fold_layer1" (default on): first GCN layer computed inside the message-passing kernels wherever the slices fit the LDS
 static int g_fold_layer1 = 1;
-// (1 = fold whenever the slices fit the LDS at all; 2 = only where every graph fits HALF of it.  Measured, round 3: with the
-// K = 32 GEMMs instead of the fold's one-workgroup-per-CU large size class DHM minibatches gain 0.4 %, mixed ones lose 1 %
-// (profiles/archive/r03_lab_fold_rule.log) -- the default stays 1)
-static bool fold_layer1(const MbView &mb, int L, int K) {
-    return g_fold_layer1 && K == 1 && L >= 2 && (g_fold_layer1 == 2 ? edge_fold_pays(mb) : edge_fold_ok(mb));
-}
+static bool fold_layer1(const MbView &mb, int L, int K) { return g_fold_layer1 && K == 1 && L >= 2 && edge_fold_ok(mb); }
 
 int node_tn(const float *A, int I, const float *Bm, int J, int64_t rows, float *slabs, int *S_out, hipStream_t st, Profiler *prof) {
     if (tn_shape_mfma_ok(I, J)) return launch_gemm_tn(A, I, Bm, J, rows, slabs, S_out, st, prof);
@@ -548,12 +540,11 @@ int slot_of_name(const upamd_model_desc &d, const Dims &x, const upamd_minibatch
 
 }  // namespace
 
-void upamd::set_fold_layer1(int on) { g_fold_layer1 = on == 2 ? 2 : (on ? 1 : 0); }
+void upamd::set_fold_layer1(int on) { g_fold_layer1 = on ? 1 : 0; }
 void upamd::set_pq_exp(int on) { g_pq_exp = on ? 1 : 0; }
 void upamd::set_side_stream(int on) { g_side_stream = on ? 1 : 0; }
-void upamd::set_side_priority(int v) { g_side_priority = (v >= 0 && v <= 2) ? v : 1; }
 void upamd::set_side_heads(int on) { g_side_heads = on ? 1 : 0; }
-void upamd::set_side_wgrad(int on) { g_side_wgrad = (on >= 0 && on <= 3) ? on : 1; }
+void upamd::set_side_wgrad(int on) { g_side_wgrad = on ? 1 : 0; }
 void upamd::set_grad_buckets(int on) { g_grad_buckets = on ? 1 : 0; }
 
 extern "C" int upamd_engine_create(const upamd_model_desc *desc, upamd_engine **out) {
@@ -1369,14 +1360,9 @@ static int backward_impl(upamd_engine *eng, const void *packed_dev, const upamd_
         const bool layer_early = early_done && l > 1 && x.K == 1 && g_side_heads && tn_shape_mfma_ok(2 * D, D);
         if (!layer_early) CK(red1.add(W(S_DBIAS + l), B, 2LL * D, 1, 2 * D, 3, 2 * D, GR(P.edge_b[l - 1]), 0, W(S_CS + l)));
         if (l > 1) {
-            // side_wgrad = 1: the weight gradient starts next to this layer's dgrad; 2: behind it, i.e. next to the NEXT layer's
-            // message-passing backward (the dgrad is launched first and the side stream waits for it)
-            if (wgrad_side && g_side_wgrad == 2) {
-                CK(launch_gemm_nt(dPQ, mb.M, 2 * D, W(S_WCATT + l - 1), D, nullptr, G, Gn, 0, st, prof));
-                std::swap(G, Gn);
-            }
+            // side_wgrad: the weight gradient starts next to this layer's dgrad
             if (wgrad_side) {
-                CK(stream_after(sc->side2, st, next_event(sc)));     // dP|dQ of this layer is complete (2: and its dgrad has run)
+                CK(stream_after(sc->side2, st, next_event(sc)));     // dP|dQ of this layer is complete
                 tn_stream = sc->side2;
                 used_side2 = true;
             }
@@ -1401,10 +1387,8 @@ static int backward_impl(upamd_engine *eng, const void *packed_dev, const upamd_
                 wgrad_done[l] = next_event(sc);
                 UPAMD_HIP(hipEventRecord(wgrad_done[l], sc->side2));
             }
-            if (!(wgrad_side && g_side_wgrad == 2)) {
-                CK(launch_gemm_nt(dPQ, mb.M, 2 * D, W(S_WCATT + l - 1), D, nullptr, G, Gn, 0, st, prof));
-                std::swap(G, Gn);
-            }
+            CK(launch_gemm_nt(dPQ, mb.M, 2 * D, W(S_WCATT + l - 1), D, nullptr, G, Gn, 0, st, prof));
+            std::swap(G, Gn);
             if (l == 2 && forked && g_side_heads && !defer && x.K == 1) {
                 // G^1 is complete: the node encoder's HBM-bound G^1^T Xp product (J = 32) goes to the side stream, next to the
                 // first layer's message-passing backward and its own dPQ_1^T Xp product

@@ -32,7 +32,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 }
 
 // ------------------------------------------------------------------------------------------ NT
-template <int BN, int WM, int WN, bool A_RM, bool C_RM, int PK, int KC = 0>      // KC != 0: K known at compile time
+template <int BN, int WM, int WN, bool A_RM, bool C_RM, int KC = 0>      // KC != 0: K known at compile time
 __global__ __launch_bounds__(256, 4) void gemm_nt_mfma_kernel(const float *__restrict__ A, int64_t M, int K, int64_t lda,
                                                            const float *__restrict__ W, int N, int64_t ldw,
                                                            const float *__restrict__ bias,
@@ -44,9 +44,9 @@ __global__ __launch_bounds__(256, 4) void gemm_nt_mfma_kernel(const float *__res
     constexpr int TI = WM / 32, TJ = WN / 32;
     constexpr int NB = (BN * 4 + 255) / 256;
     static_assert((BM / WM) * WAVES_N == 4, "4 waves per workgroup");
-    // PK = K panels (of 16) per pipeline stage / barrier (2 measured slower than 1: 106 vs 113 TFLOP/s)
-    __shared__ float As[2][PK][BM * LD];
-    __shared__ float Bs[2][PK][BN * LD];
+    // one K panel (of 16) per pipeline stage / barrier (two measured slower: 106 vs 113 TFLOP/s)
+    __shared__ float As[2][BM * LD];
+    __shared__ float Bs[2][BN * LD];
 
     // XCD-aware mapping: workgroup id -> XCD id % 8 (observed dispatch); all N-tiles of an M-tile
     // land on one XCD so the A panel is fetched from HBM once and re-read from that XCD's L2.
@@ -68,51 +68,44 @@ __global__ __launch_bounds__(256, 4) void gemm_nt_mfma_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int KS = KC ? (KC >> 4) / PK : (K >> 4) / PK;      // pipeline stages
-    float4 ra[PK][2], rb[PK][NB];
-    auto load_tiles = [&](int ks) {
+    const int KS = KC ? KC >> 4 : K >> 4;      // pipeline stages
+    float4 ra[2], rb[NB];
+    auto load_tiles = [&](int kp) {
 #pragma unroll
-        for (int pp = 0; pp < PK; ++pp) {
-            const int kp = ks * PK + pp;
+        for (int q = 0; q < 2; ++q) {
+            const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
+            const int64_t gm = m0 + row;
+            const float *src = A_RM ? A + gm * lda + kp * 16 + c4 : A + ((int64_t)kp * M + gm) * 16 + c4;
+            ra[q] = gm < M ? *reinterpret_cast<const float4 *>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
-                const int64_t gm = m0 + row;
-                const float *src = A_RM ? A + gm * lda + kp * 16 + c4 : A + ((int64_t)kp * M + gm) * 16 + c4;
-                ra[pp][q] = gm < M ? *reinterpret_cast<const float4 *>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int q = 0; q < NB; ++q) {
-                const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
-                if (e < BN * 4) {
-                    // [N][K] weights: 4 consecutive k of row n;  [K][N] weights: 4 consecutive n of row k
-                    const float *src = w_kn ? W + (int64_t)(kp * 16 + e / (BN / 4)) * ldw + n0 + (e % (BN / 4)) * 4
-                                            : W + (int64_t)(n0 + row) * ldw + kp * 16 + c4;
-                    rb[pp][q] = *reinterpret_cast<const float4 *>(src);
-                }
+        for (int q = 0; q < NB; ++q) {
+            const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
+            if (e < BN * 4) {
+                // [N][K] weights: 4 consecutive k of row n;  [K][N] weights: 4 consecutive n of row k
+                const float *src = w_kn ? W + (int64_t)(kp * 16 + e / (BN / 4)) * ldw + n0 + (e % (BN / 4)) * 4
+                                        : W + (int64_t)(n0 + row) * ldw + kp * 16 + c4;
+                rb[q] = *reinterpret_cast<const float4 *>(src);
             }
         }
     };
     auto store_tiles = [&](int buf) {
 #pragma unroll
-        for (int pp = 0; pp < PK; ++pp) {
+        for (int q = 0; q < 2; ++q) {
+            const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
+            float *d = &As[buf][row * LD + c4];
+            d[0] = ra[q].x; d[1] = ra[q].y; d[2] = ra[q].z; d[3] = ra[q].w;
+        }
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
-                float *d = &As[buf][pp][row * LD + c4];
-                d[0] = ra[pp][q].x; d[1] = ra[pp][q].y; d[2] = ra[pp][q].z; d[3] = ra[pp][q].w;
-            }
-#pragma unroll
-            for (int q = 0; q < NB; ++q) {
-                const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
-                if (e < BN * 4) {
-                    if (w_kn) {
-                        float *d = &Bs[buf][pp][(e % (BN / 4)) * 4 * LD + e / (BN / 4)];
-                        d[0] = rb[pp][q].x; d[LD] = rb[pp][q].y; d[2 * LD] = rb[pp][q].z; d[3 * LD] = rb[pp][q].w;
-                    } else {
-                        float *d = &Bs[buf][pp][row * LD + c4];
-                        d[0] = rb[pp][q].x; d[1] = rb[pp][q].y; d[2] = rb[pp][q].z; d[3] = rb[pp][q].w;
-                    }
+        for (int q = 0; q < NB; ++q) {
+            const int e = tid + 256 * q, row = e >> 2, c4 = (e & 3) * 4;
+            if (e < BN * 4) {
+                if (w_kn) {
+                    float *d = &Bs[buf][(e % (BN / 4)) * 4 * LD + e / (BN / 4)];
+                    d[0] = rb[q].x; d[LD] = rb[q].y; d[2 * LD] = rb[q].z; d[3 * LD] = rb[q].w;
+                } else {
+                    float *d = &Bs[buf][row * LD + c4];
+                    d[0] = rb[q].x; d[1] = rb[q].y; d[2] = rb[q].z; d[3] = rb[q].w;
                 }
             }
         }
@@ -124,25 +117,22 @@ __global__ __launch_bounds__(256, 4) void gemm_nt_mfma_kernel(const float *__res
     for (int ks = 0; ks < KS; ++ks) {
         const int buf = ks & 1;
         if (ks + 1 < KS) load_tiles(ks + 1);
+        const float *as = &As[buf][(wr * WM + l31) * LD + lhi];
+        const float *bs = &Bs[buf][(wc * WN + l31) * LD + lhi];
 #pragma unroll
-        for (int pp = 0; pp < PK; ++pp) {
-            const float *as = &As[buf][pp][(wr * WM + l31) * LD + lhi];
-            const float *bs = &Bs[buf][pp][(wc * WN + l31) * LD + lhi];
+        for (int s = 0; s < 8; ++s) {
+            float a[TI], b[TJ];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                float a[TI], b[TJ];
+            for (int i = 0; i < TI; ++i) a[i] = as[i * 32 * LD + 2 * s];
 #pragma unroll
-                for (int i = 0; i < TI; ++i) a[i] = as[i * 32 * LD + 2 * s];
+            for (int j = 0; j < TJ; ++j) b[j] = bs[j * 32 * LD + 2 * s];
 #pragma unroll
-                for (int j = 0; j < TJ; ++j) b[j] = bs[j * 32 * LD + 2 * s];
+            for (int i = 0; i < TI; ++i)
 #pragma unroll
-                for (int i = 0; i < TI; ++i)
-#pragma unroll
-                    for (int j = 0; j < TJ; ++j)
-                        // operands swapped on purpose: D[row = n][col = m], so a lane's 4 consecutive accumulator
-                        // registers are 4 consecutive columns of one output row -> 16-byte stores in the epilogue
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j], a[i], acc[i][j], 0, 0, 0);
-            }
+                for (int j = 0; j < TJ; ++j)
+                    // operands swapped on purpose: D[row = n][col = m], so a lane's 4 consecutive accumulator
+                    // registers are 4 consecutive columns of one output row -> 16-byte stores in the epilogue
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[j], a[i], acc[i][j], 0, 0, 0);
         }
         if (ks + 1 < KS) store_tiles(buf ^ 1);
         __syncthreads();
@@ -225,17 +215,17 @@ __device__ __forceinline__ void first_wave_stagger(int mode, int cycles) {
     while (__builtin_readcyclecounter() - t0 < wait) __builtin_amdgcn_s_sleep(32);
 }
 
-// Workgroup tile (32 TM WM) x (32 TN WN), one (32 TM) x (32 TN) output block per wave.  128 x 128 with 64 x 64 per wave
-// (4 waves) is the measured optimum of the one-block-per-wave forms: 256 x 128 / 128 x 256 with EIGHT waves are 3-5 % slower,
-// 256 x 256 (16 waves on one barrier) 14 % (profiles/archive/r02_gemm_lab.md).  TM / TN > 2 give a wave a bigger block instead (fewer
-// DMA and fragment-read instructions per MFMA at two waves per SIMD); PRIO raises the wave's priority over its MFMA burst.
-template <int WM, int WN, int TM = 2, int TN = 2, bool PRIO = false>
-__global__ __launch_bounds__(64 * WM * WN, (TM * TN > 4 ? 2 : 1)) void gemm_nt_dma2_kernel(const float *__restrict__ A, int64_t M, int K,
-                                                                    const float *__restrict__ W, int N, int64_t ldw,
-                                                                    const float *__restrict__ bias,
-                                                                    const float *__restrict__ R, float *__restrict__ C,
-                                                                    int act_tanh, float alpha, int MT, int NT, int stagger_mode,
-                                                                    int stagger_cycles, uint8_t *__restrict__ exp_flags) {
+// Workgroup tile 128 x 128, 2 x 2 waves with one 64 x 64 output block (2 x 2 MFMA tiles) each: the measured optimum.
+// 256 x 128 / 128 x 256 with EIGHT waves are 3-5 % slower, 256 x 256 (16 waves on one barrier) 14 %; a bigger block per wave
+// (64 x 128 or 128 x 64 at two waves per SIMD, with or without s_setprio over the MFMA burst) measured no better
+// (profiles/archive/r02_gemm_lab.md).
+__global__ __launch_bounds__(256, 1) void gemm_nt_dma2_kernel(const float *__restrict__ A, int64_t M, int K,
+                                                              const float *__restrict__ W, int N, int64_t ldw,
+                                                              const float *__restrict__ bias,
+                                                              const float *__restrict__ R, float *__restrict__ C,
+                                                              int act_tanh, float alpha, int MT, int NT, int stagger_mode,
+                                                              int stagger_cycles, uint8_t *__restrict__ exp_flags) {
+    constexpr int WM = 2, WN = 2, TM = 2, TN = 2;                // waves, and 32 x 32 MFMA tiles per wave, along M and N
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NW = WM * WN;
     constexpr int APANEL = BM * 16, STAGE = (BM + BN) * 16;      // floats: A panel then B panel
     constexpr int NI = (BM + BN) / 16;                           // 1 KiB LDS-DMA instructions per chunk
@@ -312,7 +302,6 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 4 ? 2 : 1)) void gemm_nt_d
             for (int j = 0; j < TN; ++j) b[g][j] = *reinterpret_cast<const float4 *>(st + boff[j][g]);
         }
         if (ks + 1 < KS) issue(ks + 1, (ks + 1) & 1);      // behind the fragment reads (hipcc drains LDS-DMA before a ds_read)
-        if (PRIO) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -328,9 +317,8 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 4 ? 2 : 1)) void gemm_nt_d
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j], av[i], acc[i][j], 0, 0, 0);
             }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
     }
-    if (TM == 2 && TN == 2 && exp_flags) {
+    if (exp_flags) {
         // exp-form store (kernels.h: PQ_EXP_LIMIT): the wave's 64 x 64 block goes out as 2^(PQ_C2 x) when every |PQ_C2 x| of
         // the block is within the limit, else unchanged with its flag raised.  Wave-local decision: no barrier; the VALU
         // is ~13 % busy in this kernel, the 64 v_exp_f32 per lane are free.
@@ -380,32 +368,30 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 4 ? 2 : 1)) void gemm_nt_d
     }
 }
 
-// which LDS-DMA configuration a plain panel-major launch uses (0 = the register-staged kernel); set through
+// whether a plain panel-major launch uses the LDS-DMA kernel (1) or the register-staged one (0); set through
 // upamd_tune("gemm_nt_dma", v) by the kernel lab / tests
 // defaults = the best configuration of the kernel lab (tools/gemm_lab*.py, profiles/archive/r02_gemm_lab.md): LDS-DMA staging,
 // three workgroups per CU (12 KB of LDS padding), first-residency-round stagger
-static int g_nt_dma_variant = 1, g_stagger_mode = 1, g_stagger_cycles = 37000, g_lds_pad = 12 * 1024;
+static int g_nt_dma = 1, g_stagger_mode = 1, g_stagger_cycles = 37000, g_lds_pad = 12 * 1024;
 static int g_nt_split = 0;                      // 0 | 6 | 9, see launch_gemm_nt_ex
 static void *g_split_scratch = nullptr;
 static int64_t g_split_scratch_bytes = 0;
 void set_gemm_nt_split(int nprod) { g_nt_split = (nprod == 6 || nprod == 9) ? nprod : 0; }
 void set_gemm_lds_pad(int bytes) { g_lds_pad = bytes; }
-void set_gemm_nt_dma_variant(int v) { g_nt_dma_variant = v; }
+void set_gemm_nt_dma(int on) { g_nt_dma = on; }
 void set_gemm_stagger(int mode, int cycles) {
     if (mode >= 0) g_stagger_mode = mode;
     if (cycles >= 0) g_stagger_cycles = cycles;
 }
 
-template <int WM, int WN, int TM = 2, int TN = 2, bool PRIO = false>
 static int launch_nt_dma2(const GemmNT &g, hipStream_t st) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
+    constexpr int BM = 128, BN = 128;
     const int MT = (int)((g.M + BM - 1) / BM), MT8 = (MT + 7) / 8 * 8, NT = g.N / BN;
     const size_t lds = sizeof(float) * 2 * (size_t)(BM + BN) * 16 + (size_t)g_lds_pad;
-    auto kern = gemm_nt_dma2_kernel<WM, WN, TM, TN, PRIO>;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), (int64_t)lds)) return rc;
-    // exp-form store: only the 64 x 64-per-wave forms, and only for a bare product
-    uint8_t *flags = (TM == 2 && TN == 2 && !g.bias && !g.R && !g.act_tanh && g.alpha == 1.f) ? g.exp_flags : nullptr;
-    hipLaunchKernelGGL(kern, dim3(MT8 * NT), dim3(64 * WM * WN), lds, st, g.A, g.M, g.K, g.W, g.N, g.ldw, g.bias, g.R, g.C,
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(gemm_nt_dma2_kernel), (int64_t)lds)) return rc;
+    // exp-form store: only for a bare product
+    uint8_t *flags = (!g.bias && !g.R && !g.act_tanh && g.alpha == 1.f) ? g.exp_flags : nullptr;
+    hipLaunchKernelGGL(gemm_nt_dma2_kernel, dim3(MT8 * NT), dim3(256), lds, st, g.A, g.M, g.K, g.W, g.N, g.ldw, g.bias, g.R, g.C,
                        g.act_tanh, g.alpha, MT, NT, g_stagger_mode, g_stagger_cycles, flags);
     if (g.exp_used) *g.exp_used = flags != nullptr;
     return 0;
@@ -419,12 +405,8 @@ bool gemm_nt_exp_store_ok(const GemmNT &g) {
     if (!gemm_nt_mfma_ok(g) || g.K % 16 != 0 || g.N % 16 != 0) return false;
     const int bn = nt_tile(g);
     if (g.K == 32 || bn != 128) return false;
-    if (g_nt_split && g_nt_dma_variant != 0 && gemm_nt_split_ok(g)) return false;
-    switch (g_nt_dma_variant) {
-        case 1: case 2: case 9: return nt_dma_ok(g);
-        case 3: case 4: return nt_dma_ok(g) && g.N % 256 == 0;
-        default: return false;
-    }
+    if (g_nt_split && g_nt_dma && gemm_nt_split_ok(g)) return false;
+    return g_nt_dma && nt_dma_ok(g);
 }
 
 int64_t gemm_exp_flag_bytes(int64_t M, int N) { return 2 * ((M + 127) / 128) * (int64_t)(N / 64 > 0 ? N / 64 : 1); }
@@ -510,26 +492,30 @@ static int nt_tile(const GemmNT &g) {
     return 32;
 }
 
-template <bool A_RM, bool C_RM, int PK>
+template <bool A_RM, bool C_RM>
 static void launch_nt_layout(const GemmNT &g, hipStream_t st, bool k32 = false) {
     const int BNsel = nt_tile(g);
     const int MT = (int)((g.M + 127) / 128);
     const int MT8 = (MT + 7) / 8 * 8;
-    if (k32) {
+    if constexpr (!A_RM && !C_RM) {             // (k32 is only ever set for panel-major operands)
+        if (k32) {
+            const int NT = g.N / 128;
+            hipLaunchKernelGGL((gemm_nt_mfma_kernel<128, 64, 64, false, false, 32>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M,
+                               g.K, g.lda, g.W, g.N, g.ldw, g.bias, g.R, g.C, g.ldc, g.act_tanh, g.alpha, MT, NT, g.w_kn ? 1 : 0);
+            return;
+        }
+    }
+    if (BNsel == 128) {
         const int NT = g.N / 128;
-        hipLaunchKernelGGL((gemm_nt_mfma_kernel<128, 64, 64, A_RM, C_RM, PK, 32>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K,
-                           g.lda, g.W, g.N, g.ldw, g.bias, g.R, g.C, g.ldc, g.act_tanh, g.alpha, MT, NT, g.w_kn ? 1 : 0);
-    } else if (BNsel == 128) {
-        const int NT = g.N / 128;
-        hipLaunchKernelGGL((gemm_nt_mfma_kernel<128, 64, 64, A_RM, C_RM, PK>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
+        hipLaunchKernelGGL((gemm_nt_mfma_kernel<128, 64, 64, A_RM, C_RM>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
                            g.W, g.N, g.ldw, g.bias, g.R, g.C, g.ldc, g.act_tanh, g.alpha, MT, NT, g.w_kn ? 1 : 0);
     } else if (BNsel == 64) {
         const int NT = g.N / 64;
-        hipLaunchKernelGGL((gemm_nt_mfma_kernel<64, 64, 32, A_RM, C_RM, PK>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
+        hipLaunchKernelGGL((gemm_nt_mfma_kernel<64, 64, 32, A_RM, C_RM>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
                            g.W, g.N, g.ldw, g.bias, g.R, g.C, g.ldc, g.act_tanh, g.alpha, MT, NT, g.w_kn ? 1 : 0);
     } else {
         const int NT = g.N / 32;
-        hipLaunchKernelGGL((gemm_nt_mfma_kernel<32, 32, 32, A_RM, C_RM, PK>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
+        hipLaunchKernelGGL((gemm_nt_mfma_kernel<32, 32, 32, A_RM, C_RM>), dim3(MT8 * NT), dim3(256), 0, st, g.A, g.M, g.K, g.lda,
                            g.W, g.N, g.ldw, g.bias, g.R, g.C, g.ldc, g.act_tanh, g.alpha, MT, NT, g.w_kn ? 1 : 0);
     }
 }
@@ -553,11 +539,11 @@ int launch_gemm_nt_ex(const GemmNT &g, hipStream_t st, Profiler *prof) {
                                            : (bn == 64 ? (rm ? "gemm_nt_64_rm" : "gemm_nt_64") : (rm ? "gemm_nt_32_rm" : "gemm_nt_32")));
     int began = prof_begin(prof, pname, st, flops, bytes);
     if (began < 0) return fail(UPAMD_E_HIP, "hipEventCreate failed");
-    const int dv = (mfma && !k32 && bn == 128) ? g_nt_dma_variant : 0;
+    const bool dma = mfma && !k32 && bn == 128 && g_nt_dma;
     int dma_rc = 1;                             // 1 = not taken
     // opt-in (tune knob "gemm_split" = 6 | 9, default 0 = exact fp32 MFMA): the K >= 64 panel-major products on the bf16
     // matrix pipe from a three-way bf16 split of both operands (gemm_split.hip); everything else is unchanged
-    if (g_nt_split && dv != 0 && gemm_nt_split_ok(g)) {
+    if (g_nt_split && dma && gemm_nt_split_ok(g)) {
         const int64_t need = gemm_nt_split_scratch_bytes(g.N, g.K);
         if (need > g_split_scratch_bytes) {      // lab knob: one lazily grown device buffer (launches are stream-ordered)
             if (g_split_scratch) (void)hipFree(g_split_scratch);
@@ -567,30 +553,16 @@ int launch_gemm_nt_ex(const GemmNT &g, hipStream_t st, Profiler *prof) {
             g_split_scratch_bytes = need;
         }
         dma_rc = launch_gemm_nt_split(g, g_split_scratch, g_nt_split, st, nullptr);
-    } else {
-        switch (dv) {
-            case 1: if (nt_dma_ok(g)) dma_rc = launch_nt_dma2<2, 2>(g, st); break;
-            case 2: if (nt_dma_ok(g)) dma_rc = launch_nt_dma2<4, 2>(g, st); break;
-            case 3: if (nt_dma_ok(g) && g.N % 256 == 0) dma_rc = launch_nt_dma2<2, 4>(g, st); break;
-            case 4: if (nt_dma_ok(g) && g.N % 256 == 0) dma_rc = launch_nt_dma2<4, 4>(g, st); break;
-            // lab: a bigger block per wave (4 waves): 64 x 128 (workgroup 128 x 256) and 128 x 64 (256 x 128), +1 = with s_setprio
-            case 5: if (nt_dma_ok(g) && g.N % 256 == 0) dma_rc = launch_nt_dma2<2, 2, 2, 4, false>(g, st); break;
-            case 6: if (nt_dma_ok(g) && g.N % 256 == 0) dma_rc = launch_nt_dma2<2, 2, 2, 4, true>(g, st); break;
-            case 7: if (nt_dma_ok(g)) dma_rc = launch_nt_dma2<2, 2, 4, 2, false>(g, st); break;
-            case 8: if (nt_dma_ok(g)) dma_rc = launch_nt_dma2<2, 2, 4, 2, true>(g, st); break;
-            case 9: if (nt_dma_ok(g)) dma_rc = launch_nt_dma2<2, 2, 2, 2, true>(g, st); break;
-            default: break;
-        }
+    } else if (dma && nt_dma_ok(g)) {
+        dma_rc = launch_nt_dma2(g, st);
     }
     if (dma_rc < 0) return dma_rc;
     if (dma_rc == 0) {
-    }
-    else if (mfma) {
-        if (g.a_rm && g.c_rm) launch_nt_layout<true, true, 1>(g, st);
-        else if (g.a_rm) launch_nt_layout<true, false, 1>(g, st);
-        else if (g.c_rm) launch_nt_layout<false, true, 1>(g, st);
-        else if (k32) launch_nt_layout<false, false, 1>(g, st, true);
-        else launch_nt_layout<false, false, 1>(g, st);
+    } else if (mfma) {
+        if (g.a_rm && g.c_rm) launch_nt_layout<true, true>(g, st);
+        else if (g.a_rm) launch_nt_layout<true, false>(g, st);
+        else if (g.c_rm) launch_nt_layout<false, true>(g, st);
+        else launch_nt_layout<false, false>(g, st, k32);
     } else {
         const int64_t total = g.M * g.N;
         hipLaunchKernelGGL(gemm_nt_generic_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, g.A, g.M, g.K, g.W, g.N,

@@ -102,10 +102,10 @@ struct GemmNT {
 int64_t gemm_exp_flag_bytes(int64_t M, int N);
 bool gemm_nt_exp_store_ok(const GemmNT &g);      // a launch of g with exp_flags set WILL write them (same choice as the launcher)
 bool gemm_nt_mfma_ok(const GemmNT &g);
-void set_gemm_nt_dma_variant(int v);
+void set_gemm_nt_dma(int on);               // tune knob "gemm_nt_dma": 1 = the LDS-DMA kernel for the plain panel-major launches, 0 = register-staged
 void set_gemm_nt_min_wgs(int v);            // tune knob "nt_min_wgs": workgroups a launch must have before the 128-wide N tile is used
-void set_gemm_stagger(int mode, int cycles);
-void set_gemm_lds_pad(int bytes);   // first-residency-round stagger of the GEMM workgroups (-1 = keep)       // kernel-lab knob: LDS-DMA configuration of the plain panel-major launches
+void set_gemm_stagger(int mode, int cycles);   // first-residency-round stagger of the GEMM workgroups (-1 = keep)
+void set_gemm_lds_pad(int bytes);              // extra dynamic LDS per LDS-DMA workgroup (sets how many share a CU)
 int launch_gemm_nt_ex(const GemmNT &g, hipStream_t st, Profiler *prof);
 // opt-in: the same product on the bf16 matrix pipe by exact 3-way operand splitting (gemm_split.hip)
 void set_gemm_nt_split(int nprod);          // tune knob: 0 (default, exact fp32 MFMA) | 6 | 9 partial products
@@ -140,15 +140,13 @@ struct FoldArgs {
     const float *Xp, *W1c, *b1c, *We, *be;
 };
 bool edge_fold_ok(const MbView &mb);        // every graph of the minibatch fits the staged (LDS-resident) size classes
-bool edge_fold_pays(const MbView &mb);      // ... and fits half the LDS (two workgroups per CU), where the fold beats the K = 32 GEMMs
 void set_fwd_h_hbm(int on);                // tune knob: large-graph size class of the forward with H left in HBM (default on)
 void set_grad_buckets(int on);             // tune knob "grad_buckets" (default 1): the backward finalises the gradient buffer range by range (engine.hip)
-void set_side_wgrad(int on);               // tune knob "side_wgrad" (default 1 = adaptive: on for minibatches of <= 98304 nodes; 0 never, 2 behind the dgrad, 3 always): GCN weight-gradient GEMMs on a side stream
-void set_side_priority(int v);             // tune knob "side_priority": priority level of the side streams created from now on (1 high, 0 normal, 2 low)
+void set_side_wgrad(int on);               // tune knob "side_wgrad" (default 1 = for minibatches of <= 98304 nodes; 0 never): GCN weight-gradient GEMMs on a side stream
 void set_side_heads(int on);               // tune knob "side_heads" (default on): the land-use pointer-head chain on the side stream
 void set_side_stream(int on);              // tune knob "side_stream" (default on): per-sample chains + grouped weight gradients on an engine-owned side stream
 void set_pq_exp(int on);                   // tune knob "pq_exp" (default on): exp-form P/Q from the GEMM epilogue + LDS-DMA stage-in
-void set_fold_layer1(int on);              // tune knob: compute the first GCN layer inside the message-passing kernels
+void set_fold_layer1(int on);              // tune knob "fold_layer1" (default 1): compute the first GCN layer inside the message-passing kernels
 int launch_edge_fwd(const PackedView &pk, const MbView &mb, int D, bool last, const float *PQ, const float *bias,
                     const float *Hin, float *Hout, float *hbarV, float *hbarE, const float *Ccur, float *FE,
                     hipStream_t st, Profiler *prof, const FoldArgs *fold = nullptr, int fe_full = 1, const uint8_t *pqflag = nullptr);

@@ -162,7 +162,7 @@ def check(rc, what=''):
 # without an override of that knob see); `tuned(overrides)` is the bracket NativeEngine puts around its calls.
 TUNE_DEFAULTS = {'gemm_nt_dma': 1, 'gemm_split': 0, 'fold_layer1': 1, 'he_fused': 1, 'side_stream': 1, 'fwd_h_hbm': 1, 'fe_half': 1,
                  'pq_exp': 1, 'bwd_nb_global': 1, 'nt_min_wgs': 128, 'tiny_fused': 1, 'tiny_threads': 1024, 'side_heads': 1,
-                 'side_wgrad': 1, 'side_priority': 1, 'grad_buckets': 1, 'gemm_lds_pad': 12 * 1024, 'gemm_stagger_mode': 1,
+                 'side_wgrad': 1, 'grad_buckets': 1, 'gemm_lds_pad': 12 * 1024, 'gemm_stagger_mode': 1,
                  'gemm_stagger_cycles': 37000}      # the library's built-in defaults (include/upamd.h, the block above upamd_tune)
 _tune_lock = threading.RLock()
 _tune_depth = threading.local()

@@ -342,8 +342,9 @@ int upamd_gemm_tn(const float *A_dev, int32_t I, int64_t lda, const float *B_dev
                   int32_t row_major, float *scratch_dev, float *out_dev, void *stream);
 
 /* Process-wide kernel-lab knobs (tools/gemm_lab.py, tests, bench.py's UPAMD_TUNE): select a kernel configuration by name; no
- * reference counterpart.  Defaults in brackets; every setting computes the same results (the tests run both sides).
- *   "gemm_nt_dma" [1]   0 = register-staged gemm_nt, k > 0 = LDS-DMA configuration k of the plain panel-major launches
+ * reference counterpart.  Defaults in brackets; every setting computes the same results (the tests run both sides).  A value
+ * outside a knob's range is refused with UPAMD_E_INVALID (gemm_nt_dma, fold_layer1 and side_wgrad take 0 or 1).
+ *   "gemm_nt_dma" [1]   plain panel-major launches on the LDS-DMA gemm_nt; 0 = the register-staged kernel
  *   "gemm_split"  [0]   6 | 9 = node GEMMs as fp32-equivalent split-bf16 products (see upamd_gemm_nt_split)
  *   "fold_layer1" [1]   first GCN layer computed inside the message-passing kernels (H_0 / PQ_1 never in HBM)
  *   "he_fused"    [1]   land-use head feature backward with its K = 32 product inside the kernel (no dFE tensor)
@@ -353,15 +354,12 @@ int upamd_gemm_tn(const float *A_dev, int32_t I, int64_t lda, const float *B_dev
  *   "pq_exp"      [1]   P/Q GEMMs of layers 2..L store 2^(C2 x) block by block (flag bytes), the message-passing kernels stage
  *                       their slices by LDS-DMA; 0 = plain P/Q, register-staged slices
  *   "bwd_nb_global" [1] backward of graphs too big for two workgroups per CU walks the neighbour ids from global memory
- *   "fold_layer1" = 2   fold only where every graph of the minibatch fits half the LDS
  *   "nt_min_wgs"  [128] workgroups a gemm_nt launch must have before the 128-wide N tile is used (tests: 1)
  *   "tiny_fused"  [1]   models with D <= 32 run the fused one-workgroup-per-graph kernels (tiny.hip); 0 = the general path
  *   "tiny_threads" [1024] threads per workgroup of the fused small-model kernels (1024: 4 waves/SIMD | 512: no scratch)
  *   "side_heads"  [1]   land-use pointer-head chain (forward: first Linear; backward: softmax / feature / weight-gradient kernels) on the side stream
- *   "side_wgrad"  [1]   GCN weight-gradient GEMMs on a second side stream: 1 = for minibatches of <= 98304 nodes, 0 never, 2 behind the
- *                       layer's dgrad GEMM, 3 always
+ *   "side_wgrad"  [1]   GCN weight-gradient GEMMs on a second side stream for minibatches of <= 98304 nodes; 0 = never
  *   "grad_buckets" [1]  upamd_backward finalises the gradient buffer range by range (upamd_grad_buckets); 0 = everything in the final flush
- *   "side_priority" [1] priority level of the side streams created from now on: 1 high, 0 normal, 2 low
  *   "gemm_lds_pad", "gemm_stagger_mode", "gemm_stagger_cycles": residency / first-round stagger of the LDS-DMA gemm_nt */
 int upamd_tune(const char *name, int32_t value);
 /* Lab hook: buf_dev = int64[32] (or NULL to switch off): the fused small-model kernel's workgroup 0 writes 100 MHz wall-clock stamps

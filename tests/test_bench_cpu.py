@@ -96,7 +96,7 @@ def test_dump_outputs_writes_the_last_steps_arrays_as_float32(tmp_path):
     import torch
     n = 10
     g = torch.Generator().manual_seed(0)
-    up = types.SimpleNamespace(engine=types.SimpleNamespace(n_floats=n), lanes=1, _lane_bufs=None,
+    up = types.SimpleNamespace(engine=types.SimpleNamespace(n_floats=n),
                                flat=torch.randn(n, generator=g), m=torch.randn(n, generator=g), v=torch.rand(n, generator=g),
                                grads=torch.randn(n + 4, generator=g), _rows=[torch.randn(6, generator=g) for _ in range(6)])
     sizes = bench.dump_outputs(str(tmp_path / 'dump'), up)

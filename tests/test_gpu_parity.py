@@ -335,7 +335,7 @@ def test_wide_model_matches_oracle(D, L, heads, n_range, T):
 
 
 @pytest.mark.parametrize('D,L,heads,n_range,T,wgrad', [(256, 3, 1, (200, 345), 24, 1), (64, 2, 2, (30, 60), 16, 1),
-                                                          (256, 3, 1, (200, 345), 24, 3), (128, 3, 4, (40, 90), 12, 2)])
+                                                          (256, 3, 1, (200, 345), 24, 0), (128, 3, 4, (40, 90), 12, 0)])
 def test_forked_step_is_bit_identical_to_the_single_stream_step(D, L, heads, n_range, T, wgrad, tune):
     """The per-sample chains and the grouped weight-gradient launch run on the engine's side stream underneath the GCN
     layers (tune knob side_stream, default on).  Same kernels, same reduction orders: values and every gradient must equal
@@ -353,7 +353,7 @@ def test_forked_step_is_bit_identical_to_the_single_stream_step(D, L, heads, n_r
         torch.cuda.synchronize()
         return [value.clone(), logp.clone(), ent.clone(), grads]
     # side_wgrad: 1 = the default (weight-gradient GEMMs on the side stream for minibatches of <= 98 k nodes: all of these),
-    # 3 = always next to the dgrad, 2 = behind it; side_heads (default on) puts the pointer-head chain there as well
+    # 0 = on the caller's stream (what larger minibatches take); side_heads (default on) puts the pointer-head chain there as well
     tune('side_wgrad', wgrad)
     tune('side_stream', 0)
     ref = run()

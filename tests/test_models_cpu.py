@@ -188,8 +188,13 @@ def test_kernel_lab_knobs_per_engine_bracket():
     finally:
         native.tune('tiny_fused', 1)
     assert fused() == 1
-    with pytest.raises(KeyError):
-        native.tune('no_such_knob', 1)
+    # unknown knobs and retired lab settings are refused, not clamped to a default: the wrapper knows no such knob (KeyError), or
+    # the library answers UPAMD_E_INVALID (RuntimeError) -- and refuses them itself as well
+    for name, value in (('no_such_knob', 1), ('side_priority', 1), ('gemm_nt_dma', 2), ('gemm_nt_dma', 9), ('side_wgrad', 2),
+                        ('side_wgrad', 3), ('fold_layer1', 2)):
+        with pytest.raises((KeyError, RuntimeError)):
+            native.tune(name, value)
+        assert native.lib().upamd_tune(name.encode(), value) == -1, (name, value)      # UPAMD_E_INVALID
     seen = {0: set(), 1: set()}
 
     def worker(v):

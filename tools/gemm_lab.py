@@ -1,6 +1,6 @@
-"""Kernel lab: the register-staged gemm_nt against the LDS-DMA kernel at every workgroup tile, on the shapes of the
-training step (needs a GPU).  Earlier lab rounds (staging variants, stagger, K sweep, occupancy x priority) are
-summarised with their raw logs in profiles/archive/r02_gemm_lab.md."""
+"""Kernel lab: the register-staged gemm_nt against the LDS-DMA kernel, each with and without the LDS padding, on the shapes of
+the training step (needs a GPU).  Earlier lab rounds (workgroup tiles, staging variants, stagger, K sweep, occupancy x priority)
+are summarised with their raw logs in profiles/archive/r02_gemm_lab.md."""
 import ctypes as C
 import os
 import sys
@@ -11,10 +11,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from drl_urban_planning_amd import native  # noqa: E402
 from kernel_bench import P, time_ms  # noqa: E402
 
-NAMES = {0: 'register-staged 128x128', 1: 'LDS-DMA 128x128 (default)', 2: 'LDS-DMA 256x128', 3: 'LDS-DMA 128x256', 4: 'LDS-DMA 256x256',
-         5: '4 waves x (64x128)', 6: '4 waves x (64x128) + setprio', 7: '4 waves x (128x64)', 8: '4 waves x (128x64) + setprio',
-         9: 'LDS-DMA 128x128 + setprio'}
-VARIANTS = tuple(int(v) for v in os.environ.get('GEMM_LAB_VARIANTS', '0,1,2,3,4').split(','))
+NAMES = {0: 'register-staged 128x128', 1: 'LDS-DMA 128x128 (default)'}
+VARIANTS = (0, 1)
 
 
 def main():

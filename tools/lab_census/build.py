@@ -81,8 +81,8 @@ patch('gemm.hip', [
     # the LDS-DMA NT kernel (slot kept in a register: this kernel has VGPRs to spare)
     ('    if (mt >= MT) return;\n    first_wave_stagger(stagger_mode, stagger_cycles);\n',
      '    if (mt >= MT) return;\n    const int census_slot = census_begin(1);\n    first_wave_stagger(stagger_mode, stagger_cycles);\n', 1),
-    ("                *reinterpret_cast<float4 *>(C + o) = make_float4(v[0] * alpha, v[1] * alpha, v[2] * alpha, v[3] * alpha);\n            }\n    }\n}\n\n// which LDS-DMA configuration",
-     "                *reinterpret_cast<float4 *>(C + o) = make_float4(v[0] * alpha, v[1] * alpha, v[2] * alpha, v[3] * alpha);\n            }\n    }\n    census_end(census_slot);\n}\n\n// which LDS-DMA configuration", 1),
+    ("                *reinterpret_cast<float4 *>(C + o) = make_float4(v[0] * alpha, v[1] * alpha, v[2] * alpha, v[3] * alpha);\n            }\n    }\n}\n\n// whether a plain panel-major launch",
+     "                *reinterpret_cast<float4 *>(C + o) = make_float4(v[0] * alpha, v[1] * alpha, v[2] * alpha, v[3] * alpha);\n            }\n    }\n    census_end(census_slot);\n}\n\n// whether a plain panel-major launch", 1),
     # the TN (weight-gradient) kernel
     ('    if (split >= S) return;\n    const int it = tile / JT, jt = tile % JT;\n',
      '    if (split >= S) return;\n    const int census_slot = census_begin(2);\n    const int it = tile / JT, jt = tile % JT;\n', 1),
@@ -93,8 +93,8 @@ patch('gemm.hip', [
 ])
 
 if NT128:
-    patch('gemm.hip', [('__global__ __launch_bounds__(64 * WM * WN, (TM * TN > 4 ? 2 : 1)) void gemm_nt_dma2_kernel',
-                        '__global__ __launch_bounds__(64 * WM * WN, 4) void gemm_nt_dma2_kernel', 1)])
+    patch('gemm.hip', [('__global__ __launch_bounds__(256, 1) void gemm_nt_dma2_kernel',
+                        '__global__ __launch_bounds__(256, 4) void gemm_nt_dma2_kernel', 1)])
 
 # message passing: the slot lives in 4 bytes of static LDS (these kernels are built for exactly 64 VGPRs)
 patch('edge.hip', [

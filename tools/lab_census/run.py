@@ -1,17 +1,18 @@
 """Co-residency lab (round 6, review item 1): does the D = 256 step ever hold an MFMA-bound GEMM workgroup and a VALU-bound
 message-passing workgroup ON THE SAME CU at the same time, and what does it do to each?  GPU box, after tools/lab_census/build.py:
 
-    python tools/lab_census/run.py --mode serial|wgrad2|two_streams [--tune knob=value,...] [--rows 2048] [--out profiles/x.json]
+    python tools/lab_census/run.py --mode serial|two_streams [--tune knob=value,...] [--rows 2048] [--out profiles/x.json]
 
   serial       the product's default step (GEMMs and walks one after the other on the caller's stream)
-  wgrad2       tune knob side_wgrad = 2: layer l's weight-gradient GEMM on a side stream NEXT TO layer l-1's message-passing backward
-  lanes        the product's opt-in UPAMD_LANES=2: one updater, every minibatch as two halves on two streams, gradients added
   two_streams  two half-minibatch steps (rows / 2 each, two engines, two streams) enqueued alternately: one half's GEMMs meet the
                other half's walks wherever the hardware dispatcher lets them -- the stream-level form of "software-pipeline two
                half-minibatches"
 
 Every mode is timed twice: on the PRODUCT library (clean step time, no census) and on the census build (one step recorded: per
-workgroup the kernel, the CU, start / end on the 100 MHz clock and the shader cycles in between)."""
+workgroup the kernel, the CU, start / end on the 100 MHz clock and the shader cycles in between).
+
+The round-6 modes `wgrad2` (side_wgrad = 2) and `lanes` (UPAMD_LANES=2) drove product switches that measured slower and were removed;
+their results stay in profiles/r06_lab_census_*."""
 import argparse
 import ctypes as C
 import json
@@ -136,7 +137,7 @@ def analyse(rec):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--mode', default='serial', choices=['serial', 'wgrad2', 'two_streams', 'lanes'])
+    ap.add_argument('--mode', default='serial', choices=['serial', 'two_streams'])
     ap.add_argument('--tune', default='')
     ap.add_argument('--rows', type=int, default=2048)
     ap.add_argument('--steps', type=int, default=12)
@@ -152,14 +153,10 @@ def main():
     from drl_urban_planning_amd import native, PPOUpdater, synth
     assert (native.LIB_PATH == census_lib) == bool(args.census)
     tune = dict(kv.split('=') for kv in args.tune.split(',') if kv)
-    if args.mode == 'wgrad2':
-        tune.setdefault('side_wgrad', '2')
     for k, v in tune.items():
         native.tune(k, int(v))
     w = dict(bench.WORKLOADS['hlg_d256'])
     dev = torch.device('cuda', 0)
-    if args.mode == 'lanes':
-        os.environ['UPAMD_LANES'] = '2'         # the PRODUCT's opt-in two-lane step (agent.PPOUpdater._step_lanes)
     lanes = 2 if args.mode == 'two_streams' else 1
     rows = args.rows // lanes
     ups, its, streams = [], [], []

@@ -20,8 +20,10 @@ from collections import defaultdict
 from csrc_hash import csrc_hash
 
 SHORT = [      # demangled (csv output) and mangled (rocpd) spellings
-    (r'gemm_nt_dma2_kernel(<2, 2|ILi2ELi2)', 'gemm_nt_128'),          # round 2: the LDS-DMA kernel is the 128 x 128 node GEMM
-    (r'gemm_nt_mfma_kernel(<128, 64, 64, false, false, 1, 32|ILi128ELi64ELi64ELb0ELb0ELi1ELi32)', 'gemm_nt_128_k32'),
+    # the LDS-DMA kernel is the 128 x 128 node GEMM: a plain kernel now, <2, 2, ...> in the traces of the templated one
+    (r'gemm_nt_dma2_kernel(\(|EPK|<2, 2|ILi2ELi2)', 'gemm_nt_128'),
+    # K = 32: <.., 32> now, <.., 1, 32> in traces from when the kernel had a PK parameter
+    (r'gemm_nt_mfma_kernel(<128, 64, 64, false, false, (1, )?32>|ILi128ELi64ELi64ELb0ELb0E(Li1E)?Li32E)', 'gemm_nt_128_k32'),
     (r'gemm_nt_mfma_kernel(<128, 64, 64, false, false|ILi128ELi64ELi64ELb0ELb0)', 'gemm_nt_128'),
     (r'gemm_nt_mfma_kernel(<128, 64, 64, true|ILi128ELi64ELi64ELb1)', 'gemm_nt_128_rm'),
     (r'gemm_nt_mfma_kernel(<64|ILi64)', 'gemm_nt_64'),
